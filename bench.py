@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Benchmark of the CURIOUS rollout-and-update hot path on MI355X (BASELINE.json metric / configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints one JSON line.  --dump-outputs DIR also writes what the last timed
+step computed (DIR/<name>.npy).  --full adds the side measurements: the per-kernel event pass and roofline, the CPU baselines,
+the reference's 19-rank regime (one GPU) and, with several ranks, the collectives and the IPC probe.
 
 One "step" = one training cycle of train.py:148-155 on MultiTaskFetchArm4-v5 dims, per GPU:
     generate_rollouts (256 GPU-resident envs x T=50)  ->  store_episode (+ normaliser update)
@@ -31,6 +35,14 @@ ENV = 'MultiTaskFetchArm4-v5'
 B_R = 256                      # parallel rollouts per GPU (configs[1])
 N_BATCHES = 100
 BATCH = 256
+CPU_RANKS_MAX = 12             # processes of the multi-process CPU baseline at most (each one imports torch)
+
+
+def _usable_cores():
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 1
 
 
 def parse():
@@ -38,9 +50,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the timed steps: per-kernel event pass + roofline, CPU baselines, the 19-rank regime line, '
+                         'collectives and IPC probe (several ranks)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-regime-line', action='store_true',
-                    help="the default run (N = 1, headline configuration, with the CPU baseline) also measures the reference's "
+                    help="a --full run (N = 1, headline configuration, with the CPU baseline) also measures the reference's "
                          "published --num_cpu 19 regime as 19 virtual ranks in a child process: skip that")
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--prefill', type=int, default=2048, help='synthetic episodes pre-loaded per buffer')
@@ -62,12 +79,15 @@ def parse():
                     help="diagnostic: 'task_experts' = BASELINE configs[4], every expert updated in one batched launch "
                          "sequence per update (curious_ddpg_update_experts)")
     ap.add_argument('--cpu-ranks', type=int, default=-1,
-                    help='ranks of the multi-process CPU baseline (default min(19, host cores); 0 = skip)')
+                    help='--full: ranks of the multi-process CPU baseline (default min(%d, usable host cores); 0 = skip)'
+                         % CPU_RANKS_MAX)
     ap.add_argument('--cpu-rank-worker', type=int, nargs=4, default=None, help=argparse.SUPPRESS)
     ap.add_argument('--ipc-probe', type=int, default=0, help=argparse.SUPPRESS)     # child mode of ipc_probe()
     ap.add_argument('--no-ipc-probe', action='store_true',
                     help='several ranks: skip the side measurement of the fused IPC all-reduce + Adam path')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.num_cpu and args.virtual_ranks > 1:
         ap.error('--num-cpu R names the ranks of the whole job, --virtual-ranks V the ranks per GPU: give one of them')
     if args.num_cpu and args.num_cpu < args.gpus:
@@ -150,8 +170,9 @@ def experts_cycle(bank, workers, k):
     i = k % len(workers)
     episode, cp, n_ep = workers[i].generate_rollouts()
     bank[i].store_episode(episode, cp, n_ep)
-    bank.train_batches(N_BATCHES)
+    losses = bank.train_batches(N_BATCHES)
     bank.update_target_net()
+    return dict(episode=episode, cp=cp, n_episodes=n_ep, losses=losses)
 
 
 def prefill(policy, n_eps, seed):
@@ -195,10 +216,70 @@ def prefill(policy, n_eps, seed):
 
 
 def cycle(policy, worker):
+    """One step; returns what its caller receives (GPU tensors / views, nothing is synchronised here)."""
     episode, cp, n_ep = worker.generate_rollouts()
     policy.store_episode(episode, cp, n_ep)
-    policy.train_batches(N_BATCHES)                               # = for _ in range(N_BATCHES): policy.train()
+    losses = policy.train_batches(N_BATCHES)                      # = for _ in range(N_BATCHES): policy.train()
     policy.update_target_net()
+    return dict(episode=episode, cp=cp, n_episodes=n_ep, losses=losses)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _flatten_outputs(name, obj, out):
+    """{name: numpy array} of a step's outputs: tensors and arrays as they are, dicts / sequences by key / index."""
+    import numpy as np
+    import torch
+    if obj is None:
+        return
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _flatten_outputs('%s_%s' % (name, k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for k, v in enumerate(obj):
+            _flatten_outputs('%s_%d' % (name, k), v, out)
+    elif isinstance(obj, torch.Tensor):
+        wide = obj.dtype == torch.float64 or not obj.dtype.is_floating_point
+        out[name] = obj.detach().to('cpu', torch.float64 if wide else torch.float32).numpy()
+    else:
+        a = np.asarray(obj)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in 'iub' else np.float32)
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes {name: array} as path/<name>.npy (float32 / float64, C order).  Above `limit` bytes in all, every array is
+    replaced by the same fixed, seeded sample of its flattened elements (sorted indices, a fraction limit / total)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= limit else limit / float(total)
+    written = 0
+    for name in sorted(arrays):
+        a = np.ascontiguousarray(arrays[name])
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            n = int(flat.size * frac)
+            idx = np.sort(np.random.RandomState(0).choice(flat.size, n, replace=False)) if n else np.zeros(0, np.int64)
+            a = flat[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+        written += a.nbytes
+    return written
+
+
+def step_outputs(last, policies):
+    """What the last timed step computed: the arrays its caller receives (episode, CP vector, episode count, the losses
+    of the last update) and the parameters it left (online and target networks of every policy)."""
+    out = {}
+    _flatten_outputs('episode', dict(last['episode']), out)
+    _flatten_outputs('cp', last['cp'], out)
+    _flatten_outputs('n_episodes', last['n_episodes'], out)
+    _flatten_outputs('losses', last['losses'], out)
+    for i, pol in enumerate(policies):
+        tag = '' if len(policies) == 1 else '_%d' % i
+        _flatten_outputs('theta' + tag, pol.theta, out)
+        _flatten_outputs('theta_target' + tag, pol.theta_target, out)
+    return out
 
 
 def kernel_flops_bytes(policy, lay, B_R=B_R, n_experts=1):
@@ -705,12 +786,12 @@ def ipc_probe(args, steps=10, timeout=100.0):
 
 
 def regime_line(args, ranks=19, steps=10, timeout=150.0):
-    """The default run's diagnostic: the reference's PUBLISHED regime (readme.md:16, `--num_cpu 19`) as 19 virtual ranks on
+    """The --full run's diagnostic: the reference's PUBLISHED regime (readme.md:16, `--num_cpu 19`) as 19 virtual ranks on
     this GPU -- the one configuration in which the chip is loaded -- measured in a child process behind the timed region
     (`bench.py --virtual-ranks 19`, a few cycles), so that the driver's own record carries it next to the headline.  A
     failure there is reported, it does not take the line with it."""
-    cmd = [sys.executable, os.path.abspath(__file__), '--virtual-ranks', str(ranks), '--steps', str(steps), '--warmup', '3',
-           '--no-cpu-baseline', '--no-regime-line']
+    cmd = [sys.executable, os.path.abspath(__file__), '--full', '--virtual-ranks', str(ranks), '--steps', str(steps),
+           '--warmup', '3', '--no-cpu-baseline', '--no-regime-line']
     if args.no_graph:
         cmd.append('--no-graph')
     env = {k: v for k, v in os.environ.items() if not k.startswith('TORCHELASTIC_')}
@@ -726,7 +807,7 @@ def regime_line(args, ranks=19, steps=10, timeout=150.0):
             return dict(error='child exited with %d: %s' % (p.returncode, errtxt.decode(errors='replace')[-300:]))
         d = json.loads([ln for ln in out.decode().splitlines() if ln.startswith('{')][-1])
         k = d.get('kernels', {})
-        return {'command': 'python bench.py --virtual-ranks %d --steps %d --warmup 3 --no-cpu-baseline' % (ranks, steps),
+        return {'command': 'python bench.py --full --virtual-ranks %d --steps %d --warmup 3 --no-cpu-baseline' % (ranks, steps),
                 'what': "the reference's --num_cpu %d job on ONE GPU: %d private buffer sets / seeds / rollout groups, every "
                         "update = %d minibatches of 256 in one launch sequence, gradients summed (diagnostic, not the headline)"
                         % (ranks, ranks, ranks),
@@ -758,8 +839,8 @@ def main():
     # the CPU legs run first, before this process touches the GPU (rank 0 of a one-GPU run only)
     cpu = None
     V = args.virtual_ranks if not (args.num_cpu and args.gpus == 1) else args.num_cpu
-    if int(os.environ.get('WORLD_SIZE', '1')) == 1 and args.gpus == 1 and not args.no_cpu_baseline:
-        n_ranks = min(19, os.cpu_count() or 1) if args.cpu_ranks < 0 else args.cpu_ranks
+    if args.full and int(os.environ.get('WORLD_SIZE', '1')) == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+        n_ranks = min(CPU_RANKS_MAX, _usable_cores()) if args.cpu_ranks < 0 else args.cpu_ranks
         if V > 1:
             # the SAME job on the host cores: R single-threaded oracle processes, 2 rollouts and batch 256 per rank,
             # gradients summed over ranks -- as many ranks as the box has cores for (stated in `cores`)
@@ -785,13 +866,14 @@ def main():
         assert not experts, '--num-cpu: the curious structure (task_experts: --virtual-ranks)'
         V, base, R_total = dist.virtual_layout(args.num_cpu)
         layout = [int(x) for x in dist.allgather_object(V)]
+    last = [None]                                                 # the outputs of the latest step
     if experts:
         params, dims, bank, workers = build_experts_job(use_graph=not args.no_graph, env=args.env, b_r=b_r, virtual_ranks=V)
         prefill(bank[0], args.prefill, seed=rank)                 # the buffers are shared by the experts
         counter = [0]
 
         def step():
-            experts_cycle(bank, workers, counter[0])
+            last[0] = experts_cycle(bank, workers, counter[0])
             counter[0] += 1
         policy, worker = bank[0], workers[0]
     else:
@@ -800,7 +882,7 @@ def main():
         prefill(policy, args.prefill, seed=rank)
 
         def step():
-            cycle(policy, worker)
+            last[0] = cycle(policy, worker)
 
     for _ in range(args.warmup):
         step()
@@ -819,6 +901,8 @@ def main():
     if world > 1:
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(last[0], list(bank) if experts else [policy]))
 
     phases = None
     if args.phases and not experts:
@@ -838,15 +922,16 @@ def main():
 
     # per-kernel HIP-event timing of the same cycle (eager launches; events cannot sit inside a replayed hipGraph)
     prof_cycles = 1
-    if experts:
+    roof = table = None
+    if args.full and experts:
         stats, overhead_ms, eager_update_ms = profile_pass(policy, worker, prof_cycles, bank=bank, step=step)
         roof, table = roofline(policy, worker, stats, prof_cycles, overhead_ms, n_experts=len(bank))
-    else:
+    elif args.full:
         stats, overhead_ms, eager_update_ms = profile_pass(policy, worker, prof_cycles)
         roof, table = roofline(policy, worker, stats, prof_cycles, overhead_ms)
 
     coll = None
-    if dist.is_distributed():
+    if args.full and dist.is_distributed():
         coll = collective_report(policy, list(bank) if experts else [policy])
         if world > 1 and not experts and not args.no_ipc_probe and os.environ.get('CURIOUS_ALLREDUCE', 'rccl') != 'ipc':
             torch.cuda.synchronize()
@@ -902,15 +987,15 @@ def main():
                        'ranks': R_total, 'ranks_per_process': layout,
                        'hipgraph': not args.no_graph, 'rng': 'device (Philox)',
                        'parallelism': 'dp%d' % world},
-            'roofline': roof,
             # SURVEY 8d whole-update figure: 47 213 algorithmic bytes per gradient transition (1 034 B of HER rows + the
             # 40 B/param of an update spread over its 256 transitions -- over V x 256 with virtual ranks)
             'step_hbm': {'bound': 'hbm', 'unit': 'GB/s', 'peak': HBM_PEAK_GBS * world,
                          'bytes_per_transition': round(bpt, 1),
                          'achieved': round(args.steps * N_BATCHES * BATCH * mb_job / elapsed * bpt / 1e9, 2),
                          'frac': round(args.steps * N_BATCHES * BATCH * n_pol / elapsed * bpt / 1e9 / HBM_PEAK_GBS, 5)},
-            'kernels': table,
         }
+        if args.full:
+            out['roofline'], out['kernels'] = roof, table
         if coll is not None:
             out['collectives'] = coll
         if phases:
@@ -919,10 +1004,10 @@ def main():
             out['reference_regime'] = regime_line(args)
         if cpu is not None:
             out['cpu_baseline'] = cpu
-        elif world > 1 or args.gpus > 1:
+        elif args.full and (world > 1 or args.gpus > 1):
             # (rank 0 at N = 1 only, as the contract says: timing the oracle here would hold N - 1 GPUs idle)
             out['cpu_baseline'] = None
-            out['cpu_baseline_note'] = 'measured on rank 0 of the N = 1 run only (python bench.py)'
+            out['cpu_baseline_note'] = 'measured on rank 0 of the N = 1 run only (python bench.py --full)'
         print(json.dumps(out), flush=True)
     teardown(list(bank) if experts else [policy], bank if experts else None)
 

@@ -138,12 +138,12 @@ def test_two_rank_update_and_normaliser_match_the_oracle_two_rank_model(mode, gr
 
 # ------------------------------------------------------------------ the scaling harness itself
 def test_bench_runs_end_to_end_on_two_ranks():
-    """`bench.py --gpus 2` exactly as the driver's scaling run launches it (torch.distributed.run, one rank per process),
+    """`bench.py --gpus 2 --full` as the driver's scaling run launches it (torch.distributed.run, one rank per process),
     with gloo in place of RCCL because both ranks share this box's one GPU: the line must carry n_gpus = 2, the
     several-rank dominant kernel, the all-reduce timed alone, the communicator's settings, identical replicas -- and
     the processes must shut down cleanly."""
-    out = _launch2([os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--prefill', '256'],
-                   _two_rank_env())
+    out = _launch2([os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--prefill', '256',
+                    '--full'], _two_rank_env())
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith('{"metric"'), out.stdout[-1500:]   # stdout = rank 0's ONE line, nothing

@@ -351,7 +351,7 @@ def test_bench_lays_the_published_ranks_out_over_the_processes():
     import json
     from test_gpu_round4 import _launch2, _two_rank_env
     out = _launch2([os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--num-cpu', '3', '--steps', '3', '--warmup', '1',
-                    '--prefill', '256', '--no-ipc-probe'], _two_rank_env())
+                    '--prefill', '256', '--no-ipc-probe', '--full'], _two_rank_env())
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith('{"metric"'), out.stdout[-1500:]
@@ -515,7 +515,7 @@ def test_several_rank_paths_of_eight_virtual_ranks_leave_the_same_bits():
 
 
 def test_bench_default_line_carries_the_reference_regime():
-    """bench.regime_line: the diagnostic the default `python bench.py` adds to its JSON line -- the reference's published
+    """bench.regime_line: the diagnostic `python bench.py --full` adds to its JSON line -- the reference's published
     `--num_cpu 19` job (readme.md:16) as 19 virtual ranks on this GPU, measured by a child process (here: 2 cycles)."""
     import sys
     import types
@@ -526,3 +526,35 @@ def test_bench_default_line_carries_the_reference_regime():
     assert r['ranks'] == 19 and r['unit'] == 'transitions/s' and r['value'] > 1e7 and r['ms_per_step'] > 0
     assert r['roofline']['bound'] == 'mfma' and 0.3 < r['roofline']['frac'] < 1.0
     assert set(r['kernels_avg_us']) >= {'ddpg_rows_kernel', 'dw_adam_her_kernel'}
+
+
+# ------------------------------------------------------------------ a plain bench run and its outputs
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` (no --full): one JSON line with the headline fields and none of
+    the side measurements, and the arrays of the last timed step in DIR -- the rollout, the CP vector, the losses of the
+    last update, both networks' parameters -- as float32 / float64, 64 MB at most."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if not k.startswith('TORCHELASTIC_')}
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'CURIOUS_FORCE_DIST'):
+        env.pop(k, None)
+    d = tmp_path / 'out'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--prefill',
+                          '256', '--dump-outputs', str(d)], env=env, cwd=str(tmp_path), capture_output=True, text=True,
+                         timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-1500:]
+    rec = json.loads(lines[0])
+    assert rec['steps'] == 2 and rec['warmup'] == 1 and rec['ms_per_step'] > 0 and rec['dtype'] == 'f32'
+    assert rec['unit'] == 'transitions/s' and rec['higher_is_better'] is True
+    assert abs(rec['value'] - 100 * 256 / (rec['ms_per_step'] * 1e-3)) < 1e-3 * rec['value']
+    assert not set(rec) & {'roofline', 'kernels', 'cpu_baseline', 'reference_regime', 'collectives'}, sorted(rec)
+    arrays = {p.name[:-4]: np.load(str(p)) for p in d.iterdir()}
+    assert {'episode_o', 'episode_u', 'cp', 'losses_0', 'losses_1', 'theta', 'theta_target'} <= set(arrays), sorted(arrays)
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays['episode_o'].shape == (256, 51, 40) and np.isfinite(arrays['episode_o']).all()
+    assert arrays['theta'].size == arrays['theta_target'].size and np.isfinite(arrays['theta']).all()
+    assert not np.array_equal(arrays['theta'], arrays['theta_target'])

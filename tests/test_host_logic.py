@@ -232,3 +232,30 @@ def test_checkpointed_worker_histories_are_length_and_tail():
     old = dict(st, task_history=[0, 1, 1], goal_history=[[1.0], [2.0]])   # a file written before the histories were cut
     ck.load_worker_state(dst, old)
     assert list(dst.task_history) == [0, 1, 1] and len(dst.goal_history) == 2
+
+
+# ------------------------------------------------------------------ bench.py --dump-outputs
+def test_bench_writes_step_outputs_as_float_arrays_within_the_limit(tmp_path):
+    """bench.write_outputs: every array as <name>.npy in float32 / float64; above the byte limit the same fixed, seeded
+    sample of every array, so that two runs are compared element for element."""
+    import sys
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    out = {}
+    bench._flatten_outputs('step', dict(o=torch.arange(12.).reshape(3, 4)[:, ::2], n=7,
+                                        losses=(torch.tensor(0.5), np.ones(3, np.float64))), out)
+    assert set(out) == {'step_o', 'step_n', 'step_losses_0', 'step_losses_1'}
+    assert out['step_o'].dtype == np.float32 and out['step_o'].tolist() == [[0, 2], [4, 6], [8, 10]]
+    assert out['step_n'].dtype == np.float64 and out['step_losses_1'].dtype == np.float64
+    assert bench.write_outputs(str(tmp_path / 'all'), out) == sum(a.nbytes for a in out.values())
+    np.testing.assert_array_equal(np.load(str(tmp_path / 'all' / 'step_o.npy')), out['step_o'])
+    big = dict(a=np.random.RandomState(1).randn(1000).astype(np.float32), b=np.arange(500, dtype=np.float64))
+    n = bench.write_outputs(str(tmp_path / 's1'), big, limit=4000)
+    assert n <= 4000
+    bench.write_outputs(str(tmp_path / 's2'), {k: v.copy() for k, v in big.items()}, limit=4000)
+    for k in big:
+        a, b = np.load(str(tmp_path / 's1' / (k + '.npy'))), np.load(str(tmp_path / 's2' / (k + '.npy')))
+        assert a.dtype == big[k].dtype and 0 < a.size < big[k].size
+        np.testing.assert_array_equal(a, b)
+        assert np.isin(a, big[k]).all()

@@ -7,7 +7,7 @@ ROUNDS=${ROUNDS:-3}
 for r in $(seq 1 $ROUNDS); do
   for spec in "$@"; do
     name=${spec%%=*}; envs=${spec#*=}
-    env $envs python bench.py --no-cpu-baseline --steps ${STEPS:-40} > $O/${name}_$r.json 2> $O/${name}_$r.err
+    env $envs python bench.py --full --no-cpu-baseline --steps ${STEPS:-40} > $O/${name}_$r.json 2> $O/${name}_$r.err
     python - "$name" "$O/${name}_$r.json" <<'PY'
 import json, sys
 try:

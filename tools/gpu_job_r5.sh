@@ -9,7 +9,7 @@ set +e
 cd $R && python -m curious_amd.build > /dev/null 2>&1
 git -C $R rev-parse HEAD > $O/head.txt 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/bench_under_rocprof.json 2> $O/stats.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_v19 -- $B --virtual-ranks 19 > $O/bench_v19_under_rocprof.json 2> $O/stats_v19.log
 S="python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline"
@@ -30,18 +30,18 @@ find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 find $O/stats_v19 -name "*kernel_stats.csv" -exec cp {} $O/bench_virtual_ranks_19_kernel_stats.csv \;
 python tools/trace_gaps.py $O/stats --tail 0.6 > $O/trace_gaps_single.txt 2>&1
 find $O -name "*_kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*.db" -delete
-timeout 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
-timeout 400 python bench.py --virtual-ranks 19 > $O/bench_virtual_ranks_19.json 2> $O/bench_virtual_ranks_19.err
-timeout 200 python bench.py --virtual-ranks 3 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_3.json 2> $O/bench_virtual_ranks_3.err
+timeout 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
+timeout 400 python bench.py --full --virtual-ranks 19 > $O/bench_virtual_ranks_19.json 2> $O/bench_virtual_ranks_19.err
+timeout 200 python bench.py --full --virtual-ranks 3 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_3.json 2> $O/bench_virtual_ranks_3.err
 export RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_auto.err | grep '^{' > $O/bench_one_rank_rccl_auto.json
-CURIOUS_FORCE_DIST=1 CURIOUS_GRAPH_ALLREDUCE=0 timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_eager.err | grep '^{' > $O/bench_one_rank_rccl_eager.json
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_task_experts_one_rank_rccl.err | grep '^{' > $O/bench_task_experts_one_rank_rccl.json
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --virtual-ranks 19 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_19_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_19_one_rank_rccl.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_auto.err | grep '^{' > $O/bench_one_rank_rccl_auto.json
+CURIOUS_FORCE_DIST=1 CURIOUS_GRAPH_ALLREDUCE=0 timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_eager.err | grep '^{' > $O/bench_one_rank_rccl_eager.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_task_experts_one_rank_rccl.err | grep '^{' > $O/bench_task_experts_one_rank_rccl.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --virtual-ranks 19 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_19_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_19_one_rank_rccl.json
 unset RANK WORLD_SIZE LOCAL_RANK MASTER_ADDR MASTER_PORT
-CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 10 --warmup 3 2> $O/bench_two_ranks_gloo_one_gpu.err | grep '^{' > $O/bench_two_ranks_gloo_one_gpu.json
-timeout 200 python bench.py --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts.json 2> $O/bench_task_experts.err
-timeout 200 python bench.py --env MultiTaskFetchArm8-v5 --rollout-batch-size 1024 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_arm8_1024env.json 2> $O/bench_arm8_1024env.err
+CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 10 --warmup 3 2> $O/bench_two_ranks_gloo_one_gpu.err | grep '^{' > $O/bench_two_ranks_gloo_one_gpu.json
+timeout 200 python bench.py --full --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts.json 2> $O/bench_task_experts.err
+timeout 200 python bench.py --full --env MultiTaskFetchArm8-v5 --rollout-batch-size 1024 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_arm8_1024env.json 2> $O/bench_arm8_1024env.err
 head -c 600 $O/bench_kernel_stats.csv; cat $O/pmc_hbm.txt | tail -20; tail -n 2 $O/*.err
 timeout 200 python tools/cycle_timeline.py 2>&1 | grep -v amdgpu.ids > $O/cycle_timeline.txt
 tools/floor2_lab > $O/floor2_lab.txt 2>&1

@@ -9,7 +9,7 @@ cd "$R" || exit 1
 python -m curious_amd.build > /dev/null 2>&1
 git -C "$R" rev-parse HEAD > "$O/head.txt" 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $B > $O/bench_under_rocprof.json 2> $O/stats.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_v19 -- $B --virtual-ranks 19 > $O/bench_v19_under_rocprof.json 2> $O/stats_v19.log
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_v3 -- $B --virtual-ranks 3 > $O/bench_v3_under_rocprof.json 2> $O/stats_v3.log
@@ -34,24 +34,24 @@ python tools/trace_gaps.py $O/stats --tail 0.6 > $O/trace_gaps_single.txt 2>&1
 find $O -name "*_kernel_trace.csv" -delete; find $O -name "*counter_collection.csv" -delete; find $O -name "*.db" -delete
 # the committed PMC passes are what bench.py's roofline.traffic reads: in place before the bench lines are taken
 cp $O/pmc_hbm_traffic.json profiles/r06_pmc_hbm_traffic.json; cp $O/pmc_hbm_traffic_virtual_ranks_19.json profiles/r06_pmc_hbm_traffic_virtual_ranks_19.json
-timeout 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
-timeout 400 python bench.py --virtual-ranks 19 > $O/bench_virtual_ranks_19.json 2> $O/bench_virtual_ranks_19.err
-for V in 2 3 4 5 6 7 8 12 16; do timeout 200 python bench.py --virtual-ranks $V --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_$V.json 2> $O/bench_virtual_ranks_$V.err; done
-timeout 200 python bench.py --num-cpu 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_num_cpu_19_one_gpu.json 2> $O/bench_num_cpu_19_one_gpu.err
-CURIOUS_ROWS16=0 timeout 200 python bench.py --virtual-ranks 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_19_eight_rows.json 2> /dev/null
-CURIOUS_DW64=1280 timeout 200 python bench.py --virtual-ranks 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_19_dw64.json 2> /dev/null
+timeout 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
+timeout 400 python bench.py --full --virtual-ranks 19 > $O/bench_virtual_ranks_19.json 2> $O/bench_virtual_ranks_19.err
+for V in 2 3 4 5 6 7 8 12 16; do timeout 200 python bench.py --full --virtual-ranks $V --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_$V.json 2> $O/bench_virtual_ranks_$V.err; done
+timeout 200 python bench.py --full --num-cpu 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_num_cpu_19_one_gpu.json 2> $O/bench_num_cpu_19_one_gpu.err
+CURIOUS_ROWS16=0 timeout 200 python bench.py --full --virtual-ranks 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_19_eight_rows.json 2> /dev/null
+CURIOUS_DW64=1280 timeout 200 python bench.py --full --virtual-ranks 19 --no-cpu-baseline --steps 20 --warmup 5 > $O/bench_virtual_ranks_19_dw64.json 2> /dev/null
 export RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_auto.err | grep '^{' > $O/bench_one_rank_rccl_auto.json
-CURIOUS_FORCE_DIST=1 CURIOUS_GRAPH_ALLREDUCE=0 timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_eager.err | grep '^{' > $O/bench_one_rank_rccl_eager.json
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_task_experts_one_rank_rccl.err | grep '^{' > $O/bench_task_experts_one_rank_rccl.json
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --virtual-ranks 19 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_19_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_19_one_rank_rccl.json
-CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --virtual-ranks 3 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_3_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_3_one_rank_rccl.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_auto.err | grep '^{' > $O/bench_one_rank_rccl_auto.json
+CURIOUS_FORCE_DIST=1 CURIOUS_GRAPH_ALLREDUCE=0 timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_one_rank_rccl_eager.err | grep '^{' > $O/bench_one_rank_rccl_eager.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_task_experts_one_rank_rccl.err | grep '^{' > $O/bench_task_experts_one_rank_rccl.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --virtual-ranks 19 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_19_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_19_one_rank_rccl.json
+CURIOUS_FORCE_DIST=1 timeout 200 python bench.py --full --virtual-ranks 3 --steps 20 --warmup 5 --no-cpu-baseline 2> $O/bench_virtual_ranks_3_one_rank_rccl.err | grep '^{' > $O/bench_virtual_ranks_3_one_rank_rccl.json
 unset RANK WORLD_SIZE LOCAL_RANK MASTER_ADDR MASTER_PORT
-CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --gpus 2 --steps 10 --warmup 3 2> $O/bench_two_ranks_gloo_one_gpu.err | grep '^{' > $O/bench_two_ranks_gloo_one_gpu.json
-CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29656 bench.py --gpus 2 --num-cpu 5 --steps 10 --warmup 3 --no-ipc-probe 2> $O/bench_two_ranks_gloo_num_cpu_5.err | grep '^{' > $O/bench_two_ranks_gloo_num_cpu_5.json
-timeout 200 python bench.py --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts.json 2> $O/bench_task_experts.err
-timeout 200 python bench.py --structure task_experts --virtual-ranks 3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts_virtual_ranks_3.json 2> $O/bench_task_experts_virtual_ranks_3.err
-timeout 200 python bench.py --env MultiTaskFetchArm8-v5 --rollout-batch-size 1024 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_arm8_1024env.json 2> $O/bench_arm8_1024env.err
+CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29655 bench.py --full --gpus 2 --steps 10 --warmup 3 2> $O/bench_two_ranks_gloo_one_gpu.err | grep '^{' > $O/bench_two_ranks_gloo_one_gpu.json
+CURIOUS_DIST_BACKEND=gloo CURIOUS_RESIDENT=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29656 bench.py --full --gpus 2 --num-cpu 5 --steps 10 --warmup 3 --no-ipc-probe 2> $O/bench_two_ranks_gloo_num_cpu_5.err | grep '^{' > $O/bench_two_ranks_gloo_num_cpu_5.json
+timeout 200 python bench.py --full --structure task_experts --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts.json 2> $O/bench_task_experts.err
+timeout 200 python bench.py --full --structure task_experts --virtual-ranks 3 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_task_experts_virtual_ranks_3.json 2> $O/bench_task_experts_virtual_ranks_3.err
+timeout 200 python bench.py --full --env MultiTaskFetchArm8-v5 --rollout-batch-size 1024 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_arm8_1024env.json 2> $O/bench_arm8_1024env.err
 head -c 600 $O/bench_kernel_stats.csv; cat $O/pmc_hbm.txt | tail -20; tail -n 2 $O/*.err
 timeout 200 python tools/cycle_timeline.py 2>&1 | grep -v amdgpu.ids > $O/cycle_timeline.txt
 # (block stamps of the weight-gradient launch: a build with -DDW_STAMPS, python tools/build_variant.py dwst -DDW_STAMPS)

@@ -2,7 +2,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3w; mkdir -p $O
 cd $R && python -m curious_amd.build > /dev/null 2>&1
 cd /tmp && export TMPDIR=/tmp
 export RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 MASTER_ADDR=127.0.0.1 MASTER_PORT=29551
-B="python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline"
+B="python3 $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline"
 CURIOUS_FORCE_DIST=1 rocprofv3 --kernel-trace --output-format csv -d $O/t_rccl -- $B > $O/rccl.json 2> $O/rccl.log
 cd $R
 python tools/trace_gaps.py $O/t_rccl --tail 0.55 > $O/t_rccl_all.txt 2>&1
