@@ -34,6 +34,13 @@ __global__ void env_reset_kernel(curious_env_cfg_t E, curious_layout_t L, int32_
       }
     }
   }
+  if (E.bias && E.bias[env_of_slot(E, e)]) {                // object 1 of a biased env: the truth is kept, o reports
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      E.truth[(int64_t)e * 3 + k] = oe[3 + k];
+      oe[3 + k] = __fadd_rn(oe[3 + k], E.bias_off[k]);
+    }
+  }
   const int task = tasks[e];
   for (int i = 0; i < AG; ++i) {
     ag[(int64_t)e * AG + i] = oe[i];
@@ -59,6 +66,7 @@ extern "C" int curious_env_reset_count(const curious_env_cfg_t* E, const curious
                                        int64_t* counter, int64_t delta, curious_stream_t stream) {
   CURIOUS_CHECK(E && L && episode && tasks && goals_raw && o && ag && g && td && staging,
                 "curious_env_reset: NULL argument");
+  if (env_bias_check(E, "curious_env_reset")) return -1;
   CURIOUS_CHECK(E->dimo <= 128, "curious_env_reset: the synthetic env handles observations of at most 128 floats");
   CURIOUS_CHECK(L->dimo == E->dimo && L->dimag == 3 * E->ntasks && L->dimg == 3 * E->ntasks &&
                     L->dimtd == E->ntasks && L->dimu == 4 && E->dimo >= 3 * E->ntasks + 4,
@@ -90,6 +98,7 @@ extern "C" int curious_env_step(const curious_env_cfg_t* E, const curious_layout
                                 int32_t off_change, int32_t off_success, double reward_eps, float* flags,
                                 curious_stream_t stream) {
   CURIOUS_CHECK(E && L && episode && tasks && u && o && ag && g && td && staging, "curious_env_step: NULL argument");
+  if (env_bias_check(E, "curious_env_step")) return -1;
   CURIOUS_CHECK(t >= 0 && t < L->T, "curious_env_step: t out of range");
   CURIOUS_CHECK(E->dimo <= 128, "curious_env_step: the synthetic env handles observations of at most 128 floats");
   if (n <= 0) return 0;

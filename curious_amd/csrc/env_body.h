@@ -17,6 +17,8 @@
 //   env_step_body() -- consts + the old observation from memory + core: the single-step form
 struct EnvConsts {
   int task; uint32_t ep_ctr;
+  bool bl;                            // the lane holds an entry of object 1 (3..5) of a biased env (curious_env_cfg_t.bias)
+  float boff;                         // its sensor offset (bias_off[lane - 3]; 0 where !bl)
   float ge_i, td_i, ag0_i;            // g[e][lane], td[e][lane], achieved goal of row 0 [lane]  (where lane is in range)
   float goal[3];                      // the goal of the env's own task
   float v_hi;                         // o[e][lane + 64] (constant during the episode) when lane + 64 < dimo
@@ -24,6 +26,21 @@ struct EnvConsts {
 
 // slot -> env (curious_env_cfg_t.wrap: a batch of slots that are the SAME envs at different episodes)
 __device__ __forceinline__ int env_of_slot(const curious_env_cfg_t& E, const int e) { return E.wrap > 0 ? e % E.wrap : e; }
+
+// Sensory perturbation (curious_env_cfg_t.bias, DESIGN "Synthetic env"): a biased env reports object 1 (entries 3..5) at
+// fl32(true + bias_off[k]); its state evolves on the true coordinates, truth[slot][k].  The working array o, ag and the
+// record hold what the agent observes, so every load of o by the policy stays as it is.
+static inline int env_bias_check(const curious_env_cfg_t* E, const char* who) {
+  CURIOUS_CHECK(!E->bias || E->truth, "%s: the observation bias (bias) needs the true-state array (truth)", who);
+  CURIOUS_CHECK(!E->bias || E->ntasks >= 2, "%s: the observation bias acts on object 1, an env of %d task(s) has none",
+                who, E->ntasks);
+  return 0;
+}
+
+// a wavefront-per-env caller only: the flag is read once and made wave-uniform
+__device__ __forceinline__ bool env_biased(const curious_env_cfg_t& E, const int e) {
+  return E.bias && __builtin_amdgcn_readfirstlane(E.bias[env_of_slot(E, e)]) != 0;
+}
 
 __device__ inline EnvConsts env_consts(const curious_env_cfg_t& E, const curious_layout_t& L,
                                        const int32_t* __restrict__ episode, const int32_t* __restrict__ tasks,
@@ -36,6 +53,8 @@ __device__ inline EnvConsts env_consts(const curious_env_cfg_t& E, const curious
   const float* ge = g + (int64_t)e * AG;
   C.task = tasks[e];
   C.ep_ctr = (uint32_t)(episode[e] - 1);
+  C.bl = env_biased(E, e) && lane >= 3 && lane < 6;
+  C.boff = C.bl ? (lane == 3 ? E.bias_off[0] : (lane == 4 ? E.bias_off[1] : E.bias_off[2])) : 0.f;   // (no dynamic index)
   C.ge_i = (lane < AG) ? ge[lane] : 0.f;
   C.td_i = (lane < E.ntasks) ? td[(int64_t)e * E.ntasks + lane] : 0.f;
   C.ag0_i = (lane < AG) ? ep0[L.off_ag + lane] : 0.f;
@@ -45,7 +64,14 @@ __device__ inline EnvConsts env_consts(const curious_env_cfg_t& E, const curious
   return C;
 }
 
+// the true value of the lane's observation entry: truth for object 1 of a biased env, the observed v otherwise
+__device__ __forceinline__ float env_truth(const curious_env_cfg_t& E, const EnvConsts& C, const int e, const int lane,
+                                           const float v) {
+  return C.bl ? E.truth[(int64_t)e * 3 + lane - 3] : v;
+}
+
 // v: o[e][lane] before the step (lanes >= dimo: ignored).  Returns o[e][lane] after the step.
+// vt: the true value of the entry (env_truth; where !C.bl it is not read), updated in place.
 // STORE = false: the step is computed (return value, `next_in`) but nothing is written to global memory -- the members of
 // a workgroup group that step the same envs redundantly (mlp_rows_res.h) leave the stores to one of them.
 // what the policy's input normalisation does to an observation entry on its way into the next step's input row
@@ -60,7 +86,7 @@ struct InNorm {
 template <bool STORE = true>
 __device__ inline float env_step_core(const curious_env_cfg_t& E, const curious_layout_t& L, int32_t env_id0,
                                       const EnvConsts& C, const float* ue /* the env's 4 action values (global or LDS) */,
-                                      int32_t t, const float v, float* __restrict__ o, float* __restrict__ ag,
+                                      int32_t t, const float v, float& vt, float* __restrict__ o, float* __restrict__ ag,
                                       float* __restrict__ staging, int32_t off_change, int32_t off_success,
                                       double reward_eps, const int e, const int lane, float* __restrict__ flags,
                                       const int n, float* next_in, const float in_clip,
@@ -84,8 +110,10 @@ __device__ inline float env_step_core(const curious_env_cfg_t& E, const curious_
   const int jt = i / 3, k = i - 3 * jt;
   // old position of the object this lane's entry belongs to (entries 3 jt .. 3 jt + 2 live in lanes 3 jt ..)
   const int ob = (i < AG) ? 3 * jt : 0;
-  const float obj0 = __shfl(v, ob), obj1 = __shfl(v, ob + 1), obj2 = __shfl(v, ob + 2);
-  float nv = v;
+  // (the state evolves on the true coordinates: w is v but on object 1 of a biased env; the gripper is never biased)
+  const float w = C.bl ? vt : v;
+  const float obj0 = __shfl(w, ob), obj1 = __shfl(w, ob + 1), obj2 = __shfl(w, ob + 2);
+  float nv = w;
   if (i < E.dimo) {
     if (i < 3) {
       nv = ng[i];
@@ -93,7 +121,7 @@ __device__ inline float env_step_core(const curious_env_cfg_t& E, const curious_
       if (jt < 4) {
         float d = fmaxf(fmaxf(fabsf(__fsub_rn(grip[0], obj0)), fabsf(__fsub_rn(grip[1], obj1))),
                         fabsf(__fsub_rn(grip[2], obj2)));
-        if (d < 0.1f && uc[3] < 0.0f) nv = fclip(__fadd_rn(v, delta[k]), -1.0f, 1.0f);
+        if (d < 0.1f && uc[3] < 0.0f) nv = fclip(__fadd_rn(w, delta[k]), -1.0f, 1.0f);
       } else {
         Philox4 r = philox4x32((uint32_t)(env_id0 + env_of_slot(E, e)), C.ep_ctr, (uint32_t)(t * E.ntasks + jt), STREAM_DISTRACT,
                                (uint32_t)E.seed, (uint32_t)(E.seed >> 32));
@@ -105,6 +133,10 @@ __device__ inline float env_step_core(const curious_env_cfg_t& E, const curious_
       nv = delta[i - AG];
     } else if (i == AG + 3) {
       nv = uc[3];
+    }
+    if (C.bl) {                                             // what goes out from here on is what the sensor reports
+      vt = nv;
+      nv = __fadd_rn(nv, C.boff);
     }
     if (next_in) {
       float w = (in_clip > 0.f) ? fclip(nv, -in_clip, in_clip) : nv;
@@ -127,6 +159,7 @@ __device__ inline float env_step_core(const curious_env_cfg_t& E, const curious_
       row[off_change + i] = (fabsf(__fsub_rn(C.ag0_i, nv)) > 1e-3f) ? 1.0f : 0.0f;             // rollout.py:284
       row[L.off_g + i] = C.ge_i;
     }
+    if (C.bl) E.truth[(int64_t)e * 3 + i - 3] = vt;
     if (i < L.dimu) row[L.off_u + i] = ue[i];
     if (i < E.ntasks) row[L.off_td + i] = C.td_i;
   }
@@ -165,6 +198,7 @@ __device__ inline void env_step_body(const curious_env_cfg_t& E, const curious_l
                                      float* __restrict__ flags = nullptr, const int n = 0) {
   const EnvConsts C = env_consts(E, L, episode, tasks, o, g, td, staging, e, lane);
   const float v = (lane < E.dimo) ? o[(int64_t)e * E.dimo + lane] : 0.f;
-  (void)env_step_core(E, L, env_id0, C, ue, t, v, o, ag, staging, off_change, off_success, reward_eps, e, lane, flags, n,
+  float vt = env_truth(E, C, e, lane, v);
+  (void)env_step_core(E, L, env_id0, C, ue, t, v, vt, o, ag, staging, off_change, off_success, reward_eps, e, lane, flags, n,
                       nullptr, 0.f);
 }

@@ -188,6 +188,7 @@ static int policy_act_env_steps(const curious_net_cfg_t* cfg, const float* theta
   if (rgp && rgp->group > 0) { rg.group = rgp->group; rg.seed_stride = rgp->seed_stride; rg.exploit = rgp->exploit; }
   CURIOUS_CHECK(theta && workspace && u_out && E && L && episode && tasks && o && ag && g && td && staging,
                 "curious_policy_act_env_step: NULL argument");
+  if (env_bias_check(E, "curious_policy_act_env_step")) return -1;
   CURIOUS_CHECK(cfg->modular, "curious_policy_act_env_step: modular nets only (use curious_policy_forward otherwise)");
   CURIOUS_CHECK(!cfg->normalize_obs || (o_stats && g_stats),
                 "curious_policy_act_env_step: input normalisation needs the statistics (curious_policy_*_stats)");

@@ -93,6 +93,7 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(ActRowsArgs a) {
     // what does not change during the episode, and the env's observation (lane l: entry l) carried in a register
     const EnvConsts ec = env_consts(a.E, a.L, a.episode, a.tasks, a.eo, a.g, a.td, a.staging, m, x.lane);
     float ov = (x.lane < a.E.dimo) ? a.eo[(int64_t)m * a.E.dimo + x.lane] : 0.f;
+    float ovt = env_truth(a.E, ec, m, x.lane, ov);           // (its true value: object 1 of a biased env)
     // The exploration noise does not depend on the policy output.  Drawing it inside the step would occupy the wave with
     // 4 active lanes (Philox + float64 Box-Muller) once per step; instead all 64 lanes draw the noise of ALL steps of
     // this wave's env up front -- draw q = 4 s + d: step s, action component d -- into LDS.  (Same (index, counter)
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void policy_rows_kernel(ActRowsArgs a) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      ov = env_step_core(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, a.eo, a.eag, a.staging, a.off_change,
+      ov = env_step_core(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, ovt, a.eo, a.eag, a.staging, a.off_change,
                          a.off_success, a.reward_eps, m, x.lane, a.flags, a.n,
                          (s + 1 < a.nsteps) ? x.xin + x.wave * XLD : nullptr, a.clip,
                          InNorm{a.o_mean, a.o_std, a.nclip, a.ag ? Sc : -1, a.g_mean, a.g_std});

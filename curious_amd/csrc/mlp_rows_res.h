@@ -177,6 +177,7 @@ __global__ __launch_bounds__(256) void policy_resident_kernel(ActRowsArgs a, Res
   const uint64_t ctr0 = a.counter + (a.counter_base ? (uint64_t)*a.counter_base : 0ull);
   const EnvConsts ec = env_consts(a.E, a.L, a.episode, a.tasks, a.eo, a.g, a.td, a.staging, m, x.lane);
   float ov = (x.lane < a.E.dimo) ? a.eo[(int64_t)m * a.E.dimo + x.lane] : 0.f;
+  float ovt = env_truth(a.E, ec, m, x.lane, ov);             // (its true value: object 1 of a biased env)
   double* nz = nzb + (size_t)x.wave * 3 * 4 * RES_NOISE_CH;
   const RowNoise rn = row_noise(a.rg, __builtin_amdgcn_readfirstlane(m), a.seed, a.noise_scale, a.random_eps);
   unsigned long long* xg = rx.xbuf + (size_t)group * 2 * 4 * 256;
@@ -257,11 +258,11 @@ __global__ __launch_bounds__(256) void policy_resident_kernel(ActRowsArgs a, Res
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     float* nin = (s + 1 < a.nsteps) ? x.xin + x.wave * XLD : nullptr;
     if (member == 0)
-      ov = env_step_core<true>(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, a.eo, a.eag, a.staging, a.off_change,
+      ov = env_step_core<true>(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, ovt, a.eo, a.eag, a.staging, a.off_change,
                                a.off_success, a.reward_eps, m, x.lane, a.flags, a.n, nin, a.clip,
                                InNorm{a.o_mean, a.o_std, a.nclip, a.ag ? Sc : -1, a.g_mean, a.g_std});
     else
-      ov = env_step_core<false>(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, a.eo, a.eag, a.staging, a.off_change,
+      ov = env_step_core<false>(a.E, a.L, a.env_id0, ec, s_u, a.t + s, ov, ovt, a.eo, a.eag, a.staging, a.off_change,
                                 a.off_success, a.reward_eps, m, x.lane, a.flags, a.n, nin, a.clip,
                                 InNorm{a.o_mean, a.o_std, a.nclip, a.ag ? Sc : -1, a.g_mean, a.g_std});
     RES_STAMP(6);

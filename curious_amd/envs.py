@@ -23,6 +23,9 @@ ENV_CONFIGS = {
     'MultiTaskFetchArm8-v5': (8, 52, 50),
 }
 REWARD_EPS = 0.05
+# the perturbation study's broken sensor (DESIGN "Synthetic env"): a biased env reports object 1 (observation / achieved-goal
+# entries 3..5) at fl32(true + BIAS_OFF), max-norm 0.15 > the grasp radius 0.1
+BIAS_OFF = (0.15, -0.15, 0.0)
 
 
 class _Space:
@@ -116,12 +119,15 @@ class ResidentRolloutVoid(_lib.CuriousHipError):
 
 
 class BatchedSyntheticArm(ArmSpec):
-    def __init__(self, name, n, seed=0, env_id0=0, T=None, pad_to=1, wrap=0):
+    def __init__(self, name, n, seed=0, env_id0=0, T=None, pad_to=1, wrap=0, bias=False, bias_mask=None):
         """pad_to: the batch is filled up to a multiple of it with idle envs (they step like any other env, nobody
         reads their episodes): the one-launch rollout kernels take whole groups of 4 envs, and 19 virtual ranks x 2
         rollouts (the reference's regime, readme.md:16) are 38.  n_used = the envs that count, n = the envs launched.
         wrap > 0: a batch of SLOTS (curious_env_cfg_t.wrap) -- slot i is env env_id0 + i % wrap at the episode episode[i]:
-        several rollouts of the same envs side by side (RolloutWorker.generate_eval_rollouts)."""
+        several rollouts of the same envs side by side (RolloutWorker.generate_eval_rollouts).
+        bias: attach the observation-bias arrays now (all envs unbiased): set_bias is then a device write that launches
+        captured earlier see.  bias_mask: the int32 per-env flags of another batch to follow (a wrapped batch of slots
+        shares the mask of the envs it wraps).  Neither: the bias pointers stay NULL until set_bias."""
         super().__init__(name)
         if T is not None:
             self.T = self._max_episode_steps = int(T)
@@ -152,7 +158,11 @@ class BatchedSyntheticArm(ArmSpec):
         self._pin_events = [None] * len(self._pins)
         self._pin_k = 0
         self._goals_dev = self._tg_dev[n:].view(n, 3)
+        self.bias_mask = self._truth = None
+        self.bias_host = np.zeros(self._wrap if self._wrap > 0 else n, np.int32)
         self._cfg = ops.make_env_cfg(self.nb_tasks, self.dimo, self.T, self._seed, self._wrap)
+        if bias or bias_mask is not None:
+            self._attach_bias(bias_mask)
         # rollout flags written by the last env step: is_success per env + one "an observation is NaN" word
         self.flags = torch.zeros(n + 1, dtype=torch.float32, device=dev)
         self._flags_pin = torch.zeros(n + 1, dtype=torch.float32).pin_memory()
@@ -164,8 +174,46 @@ class BatchedSyntheticArm(ArmSpec):
 
     def seed(self, seed):
         self._seed = int(seed)
-        self._cfg = ops.make_env_cfg(self.nb_tasks, self.dimo, self.T, self._seed, self._wrap)
+        self._cfg = ops.make_env_cfg(self.nb_tasks, self.dimo, self.T, self._seed, self._wrap, bias=self.bias_mask,
+                                     truth=self._truth, bias_off=BIAS_OFF)
         self.episode.zero_()
+
+    # ---------------------------------------------------------- sensory perturbation (train.py:142-146)
+    def _attach_bias(self, mask=None):
+        if self.nb_tasks < 2:
+            raise ValueError('%s: the observation bias acts on object 1, an env of %d task(s) has none'
+                             % (self.name, self.nb_tasks))
+        nenv = self._wrap if self._wrap > 0 else self.n
+        if mask is None:
+            mask = torch.zeros(nenv, dtype=torch.int32, device=self.device)
+        assert mask.dtype == torch.int32 and mask.numel() == nenv, 'bias_mask: int32 [%d]' % nenv
+        self.bias_mask = mask
+        self._truth = torch.zeros([self.n, 3], dtype=torch.float32, device=self.device)
+        # (in place: whoever holds a pointer to the cfg -- the torch-op descriptor -- sees the switch)
+        self._cfg.bias, self._cfg.truth = ops.ptr(self.bias_mask), ops.ptr(self._truth)
+        self._cfg.bias_off[:] = [float(np.float32(b)) for b in BIAS_OFF]
+
+    def set_bias(self, indices):
+        """Envs `indices` (of the n_used that count; idle padding envs never) report object 1 through the broken sensor
+        from their next reset on.  Returns True when the bias arrays were attached just now: launches captured before
+        hold NULL pointers and must be captured again."""
+        nenv = self.bias_host.shape[0]
+        idx = np.asarray(list(indices), dtype=np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= min(nenv, self.n_used)):
+            raise IndexError('set_bias: env indices %s out of range (%d envs)' % (idx.tolist(), min(nenv, self.n_used)))
+        attached = self.bias_mask is None
+        if attached:
+            self._attach_bias()
+        m = np.zeros(nenv, np.int32)
+        m[idx] = 1
+        self.bias_host = m
+        self.bias_mask.copy_(torch.from_numpy(m))
+        return attached
+
+    def clear_bias(self):
+        self.bias_host = np.zeros_like(self.bias_host)
+        if self.bias_mask is not None:
+            self.bias_mask.zero_()
 
     def reset_all(self, tasks, goals_raw, launch=True):
         """tasks[n] int, goals_raw[n,3] in [-1,1] (rollout.py:120-143 for every env at once).  launch=False: only the
@@ -250,6 +298,19 @@ class SyntheticArmEnv(ArmSpec):
     def unwrapped(self):
         return self
 
+    @property
+    def bias(self):
+        """The perturbation study's switch (train.py:145-146 `env.unwrapped.bias = True`): from the next reset on the env
+        reports object 1 through the broken sensor (BIAS_OFF)."""
+        return bool(self._b.bias_host[0])
+
+    @bias.setter
+    def bias(self, on):
+        if on:
+            self._b.set_bias([0])
+        else:
+            self._b.clear_bias()
+
     def seed(self, seed=None):
         self._b.seed(seed)
 
@@ -300,11 +361,13 @@ class EnvFactory:
     def __init__(self, name):
         self.name = name
         self._count = 0
+        self.bias = False        # a perturbation study: batches come with the observation-bias arrays attached (all off)
 
     def __call__(self):
         e = SyntheticArmEnv(self.name, env_id=self._count)
         self._count += 1
         return e
 
-    def make_batched(self, n, env_id0=0, pad_to=1, wrap=0):
-        return BatchedSyntheticArm(self.name, n, env_id0=env_id0, pad_to=pad_to, wrap=wrap)
+    def make_batched(self, n, env_id0=0, pad_to=1, wrap=0, bias_mask=None):
+        return BatchedSyntheticArm(self.name, n, env_id0=env_id0, pad_to=pad_to, wrap=wrap, bias=self.bias,
+                                   bias_mask=bias_mask)

@@ -97,7 +97,7 @@ class Checkpointer:
 
 def _train(policy, rollout_worker, evaluator, n_epochs, n_test_rollouts, n_cycles, n_batches, policy_save_interval,
            save_policies, structure, task_selection, params, perturbation_study=False, expert_bank=None,
-           checkpointer=None, resumed=None, **kwargs):
+           checkpointer=None, resumed=None, perturb_epoch=250, **kwargs):
     """train.py:49-166.  expert_bank (task_experts only): update ALL experts in one batched launch sequence after
     every rollout (BASELINE configs[4]) instead of only the expert that collected it.
     checkpointer: writes the resumable state (Checkpointer); resumed = (epoch, loop dict) of the checkpoint this job was
@@ -175,7 +175,8 @@ def _train(policy, rollout_worker, evaluator, n_epochs, n_test_rollouts, n_cycle
             logger.info('Starting new epoch ', epoch, 'at time', time.time() - t0)
             t_ep = time.time()
             rollout_worker.clear_history()
-            if perturbation_study and (epoch == 250 or (epoch > 250 and epoch == first_epoch)):   # (a job resumed past it)
+            if perturbation_study and (epoch == perturb_epoch or (epoch > perturb_epoch and epoch == first_epoch)):
+                # (epoch > perturb_epoch: a job resumed past it)
                 perturb_envs(rollout_worker, evaluator)              # train.py:142-146
             for cyc in range(n_cycles):                               # train.py:148-155 -- the hot loop
                 ft.tick()
@@ -198,8 +199,24 @@ def _train(policy, rollout_worker, evaluator, n_epochs, n_test_rollouts, n_cycle
 def perturb_envs(rollout_worker, evaluator, n=2):
     """The perturbation study's switch (train.py:142-146): from epoch 250 on the first two envs of the training worker and
     of the evaluator return biased observations (`env.unwrapped.bias = True`; what the bias does is the env's business --
-    gym_flowers upstream).  An env object without a `bias` attribute cannot honour it: refused, not ignored."""
+    gym_flowers upstream; here: DESIGN "Synthetic env").  An env object without a `bias` attribute cannot honour it:
+    refused, not ignored.  The GPU-resident batched env (a worker's `benv` with `set_bias`) holds rollout_batch_size envs
+    per virtual rank: envs 0 and 1 of every rank, local indices v * rollout_batch_size + {0, 1}, are biased."""
     for worker in (rollout_worker, evaluator):
+        benv = getattr(worker, 'benv', None)
+        if benv is not None and hasattr(benv, 'set_bias'):
+            B, V = int(worker.rollout_batch_size), int(getattr(worker, 'V', 1) or 1)
+            if B < n:
+                raise NotImplementedError('--perturb biases envs 0..%d of every rank: rollout_batch_size %d is too small'
+                                          % (n - 1, B))
+            if benv.set_bias([v * B + i for v in range(V) for i in range(n)]):
+                # the bias arrays were attached just now: rollouts captured before hold NULL pointers
+                pols = worker.policy if isinstance(worker.policy, (list, tuple)) else [worker.policy]
+                for pol in pols:
+                    if hasattr(pol, 'drop_rollout_graphs'):
+                        pol.drop_rollout_graphs()
+                worker.__dict__.pop('_eval_env', None)
+            continue
         envs = list(worker.envs)
         if len(envs) < n:
             raise NotImplementedError('--perturb needs a Python list of at least %d envs per worker (host envs); the '
@@ -263,12 +280,13 @@ def logs(rollout_worker, evaluator, epoch, best_success_rate, best_policy_path, 
 
 def launch(env, trial_id, n_epochs, num_cpu, seed, policy_save_interval, clip_return, normalize_obs, structure,
            task_selection, goal_selection, goal_replay, task_replay, perturb=False, save_policies=True,
-           override_params=None, save_root='./save/', resume=None, checkpoint_interval=None):
+           override_params=None, save_root='./save/', resume=None, checkpoint_interval=None, perturb_epoch=250):
     """train.py:217-339.
     resume: the log directory of an earlier job of the SAME configuration (its save_root/env/trial directory): the job goes
     on behind that job's last complete checkpoint (curious_amd.checkpoint) -- same directory, progress.csv continued -- up
     to epoch n_epochs - 1.  checkpoint_interval: epochs between checkpoints (default: policy_save_interval, the
-    reference's save cadence train.py:195-205; 0: none)."""
+    reference's save cadence train.py:195-205; 0: none).  perturb: the perturbation study (train.py:142-146), switched on
+    at epoch perturb_epoch (the reference's 250)."""
     global t0
     dist.init_from_env()
     rank = dist.rank()
@@ -329,7 +347,8 @@ def launch(env, trial_id, n_epochs, num_cpu, seed, policy_save_interval, clip_re
     params['time'] = str(datetime.datetime.now())
     params.update(env_name=env, task_selection=task_selection, goal_selection=goal_selection, task_replay=task_replay,
                   goal_replay=goal_replay, structure=structure, normalize_obs=normalize_obs, num_cpu=num_cpu,
-                  clip_return=clip_return, trial_id=trial_id, seed=seed)
+                  clip_return=clip_return, trial_id=trial_id, seed=seed, perturb=bool(perturb),
+                  perturb_epoch=int(perturb_epoch))
     if override_params:
         params.update(override_params)
     params['virtual_ranks'] = V
@@ -347,6 +366,10 @@ def launch(env, trial_id, n_epochs, num_cpu, seed, policy_save_interval, clip_re
         with open(os.path.join(logger.get_dir(), 'params.json'), 'w') as f:
             json.dump(plain, f)
     params = config.prepare_params(params)
+    if perturb and hasattr(params['make_env'], 'make_batched'):
+        # the batches come with the observation-bias arrays attached (all off): the switch is then a device write that the
+        # captured rollouts see
+        params['make_env'].bias = True
     params['ddpg_params']['normalize_obs'] = normalize_obs
     params['ddpg_params'].setdefault('seed', seed)                    # identical initial weights on every rank
     if rank == 0:
@@ -415,7 +438,7 @@ def launch(env, trial_id, n_epochs, num_cpu, seed, policy_save_interval, clip_re
                  n_epochs=n_epochs, n_test_rollouts=params['n_test_rollouts'], n_cycles=params['n_cycles'],
                  n_batches=params['n_batches'], perturbation_study=perturb, policy_save_interval=policy_save_interval,
                  save_policies=save_policies, structure=structure, task_selection=task_selection, params=params,
-                 expert_bank=expert_bank, checkpointer=checkpointer, resumed=resumed)
+                 expert_bank=expert_bank, checkpointer=checkpointer, resumed=resumed, perturb_epoch=perturb_epoch)
     shutdown(policy if isinstance(policy, list) else [policy], expert_bank)
     return best
 
@@ -459,6 +482,8 @@ def main(argv=None):
     parser.add_argument('--goal_replay', type=str, default=GOAL_REPLAY)
     parser.add_argument('--task_replay', type=str, default=TASK_REPLAY)
     parser.add_argument('--perturb', type=lambda s: s.lower() in ('1', 'true', 'yes'), default=False)
+    parser.add_argument('--perturb_epoch', type=int, default=250,
+                        help='epoch at which --perturb biases the sensor of envs 0 and 1 of every rank (train.py:142)')
     parser.add_argument('--resume', type=str, default=None,
                         help='log directory of an earlier job with the same flags (save/<env>/<trial>/): go on behind its last '
                              'complete checkpoint, bit for bit what the uninterrupted job would have computed')

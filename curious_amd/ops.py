@@ -381,9 +381,14 @@ def param_checksum(theta, out):
           'curious_param_checksum')
 
 
-def make_env_cfg(ntasks, dimo, T, seed, wrap=0):
+def make_env_cfg(ntasks, dimo, T, seed, wrap=0, bias=None, truth=None, bias_off=(0.15, -0.15, 0.0)):
+    """bias: int32 per-env flags on the device (None: the observation bias is off -- NULL), truth: float32 [slots, 3] on
+    the device (the true coordinates of object 1 of the biased envs), bias_off: the sensor offset (include/curious_hip.h)."""
     e = _lib.EnvCfg()
     e.ntasks, e.dimo, e.T, e.seed, e.wrap = int(ntasks), int(dimo), int(T), int(seed) & 0xFFFFFFFFFFFFFFFF, int(wrap)
+    if bias is not None:
+        e.bias, e.truth = ptr(bias), ptr(truth)
+        e.bias_off[:] = [float(np.float32(b)) for b in bias_off]
     return e
 
 

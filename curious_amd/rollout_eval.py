@@ -55,7 +55,9 @@ class EvalRolloutsMixin:
         per = max(2, min(n, self.EVAL_SLOTS // nB))               # rollouts per launch
         big = self.__dict__.get('_eval_env')
         if big is None or big.n != per * nB:
-            big = self.make_env.make_batched(per * nB, env_id0=env.env_id0, wrap=nB)
+            # (the slots follow the observation-bias flags of the envs they wrap: the same device mask)
+            kw = {} if getattr(env, 'bias_mask', None) is None else dict(bias_mask=env.bias_mask)
+            big = self.make_env.make_batched(per * nB, env_id0=env.env_id0, wrap=nB, **kw)
             big.seed(env._seed)
             self._eval_env = big
             self._eval_slot_k = torch.arange(per, dtype=torch.int32, device=big.device).repeat_interleave(nB)

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define CURIOUS_ABI_VERSION 10     /* bumped whenever a prototype or struct below changes */
+#define CURIOUS_ABI_VERSION 11     /* bumped whenever a prototype or struct below changes */
 #define CURIOUS_MAX_TASKS 16
 #define CURIOUS_MAX_TASK_DIMS 8
 
@@ -517,6 +517,16 @@ typedef struct curious_env_cfg {
                    * i is env env_id0 + i % wrap at an episode of its own (episode[i]): the n_test_rollouts evaluation rollouts
                    * of train.py:156-158, rollout k of env e = slot k * wrap + e, stepped by one launch instead of one per rollout */
   uint64_t seed;
+  /* Sensory perturbation (ABI 11; DESIGN "Synthetic env"): a broken sensor on object 1 (observation / achieved-goal
+   * entries 3..5).  bias == NULL: off, and every number is what ABI 10 computed (a zero-initialised struct is "off").
+   * bias[i] != 0 (one int32 per ENV, indexed like the env ids: slot i of a wrapped batch reads bias[i % wrap]): env i
+   * reports object 1 at fl32(true + bias_off[k]), k = 0..2, in o, ag, the record rows, the change flags, is_success and
+   * the next policy input, while its state evolves on the true coordinates, kept in truth[i][3] (one row per SLOT;
+   * written by curious_env_reset, read and written by every step).  bias needs truth and ntasks >= 2. */
+  const int32_t* bias;
+  float* truth;
+  float bias_off[3];
+  int32_t pad_;
 } curious_env_cfg_t;
 
 /* Reset n envs: o[n][dimo] from Philox stream (env_id0+i, episode[i]); episode[i] (episodes started so far) is
